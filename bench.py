@@ -18,7 +18,8 @@ Prints ONE JSON line on rank 0 (contract in the task description), with `rooflin
 HBM-bound integer work) and `cpu_baseline` (the CPU oracle, a port, on this box's host cores), plus `step_ms` (min / median
 / max over the timed steps) and, at N=1, `e2e_fastq_reads_per_s` / `e2e_fastq_gz_reads_per_s`: the whole FASTQ pipeline
 (lib/nimble: parse, H2D, call, TSV) on a bounded file, and `e2e_bam_reads_per_s`: the BAM pipeline on a synthetic 10x-style
-BAM, all outside the timed value.
+BAM, all outside the timed value.  `--dump-outputs DIR` writes the table of the last timed step as .npy arrays (dump_outputs):
+the reads are seeded, so two builds can be compared row for row.
 """
 import argparse
 import importlib
@@ -37,6 +38,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec); ~6.3 TB/s achievable
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 WORKLOADS = {
     "configs2": dict(features=1000, family=4, paired=False, reads=10_000_000, total=False,
@@ -151,6 +153,29 @@ def e2e_bam(pairs):
         subprocess.run(["rm", "-rf", d])
 
 
+def dump_outputs(dirpath, table, names, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the table of one step, the (callset, count) rows a caller of score::call receives, as float64 arrays
+    (every value is a whole number below 2^53, so the form is exact): `counts` = the count of each row, in row order;
+    `callset_features` = the rows' callsets one after the other, a feature being its position in the library;
+    `callset_offsets` = where they start (row i holds callset_features[callset_offsets[i]:callset_offsets[i + 1]]);
+    `row_index` = the number of each written row in the table: all of them, or, where the table would take more than
+    `limit` bytes, a sample drawn with a fixed seed (the same rows for the same table)."""
+    pos = {nm: i for i, nm in enumerate(names)}
+    cost = 8 * (np.array([len(f) for f, _ in table], dtype=np.int64) + 3)  # features + count, offset and row number
+    room = limit - 8 - 4 * 128  # the last offset and the four .npy headers
+    keep = np.arange(len(table))
+    if cost.sum() > room:
+        order = np.random.default_rng(0).permutation(len(table))
+        keep = np.sort(order[np.cumsum(cost[order]) <= room])
+    sets = [[pos[f] for f in table[i][0]] for i in keep]
+    os.makedirs(dirpath, exist_ok=True)
+    for name, values in (("counts", [table[i][1] for i in keep]),
+                         ("callset_features", [p for s in sets for p in s]),
+                         ("callset_offsets", np.cumsum([0] + [len(s) for s in sets])),
+                         ("row_index", keep)):
+        np.save(os.path.join(dirpath, name + ".npy"), np.asarray(values, dtype=np.float64))
+
+
 def native_leg(nim, synth, torch, lib_obj, seqs, devices, n, L, n_sets, warmup, steps):
     """The multi-GPU step through the C ABI alone (include/nimble_hip.h nimble_comm_* / nimble_steps_*, RCCL inside the
     device library; include/nimble_host.h nimble_multi_steps): ONE process, one native host thread per device, reads
@@ -218,6 +243,9 @@ def main():
                     help="reads of the end-to-end FASTQ runs at N=1, plain and .gz (0 = skip)")
     ap.add_argument("--e2e-bam-pairs", type=int, default=1_000_000,
                     help="read pairs of the end-to-end BAM run at N=1 (0 = skip); skipped with --e2e-reads 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the table of the last timed step to DIR as .npy arrays (see "
+                         "dump_outputs); the reads are seeded, so the same arguments give the same table on every run")
     args = ap.parse_args()
     # under a profiler the end-to-end leg is left out: it writes a FASTQ file, gzips it and starts lib/nimble children that
     # inherit the profiler's preload (their kernels would land in the counter files, and the run outlasts its timeout)
@@ -249,10 +277,6 @@ def main():
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
-    # HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue run
-    # in order: with the launch stream, the result stream, torch's streams and RCCL's, the exchange of the multi-GPU
-    # pipeline would queue behind the align kernel it is meant to overlap.  Must be set before HIP initialises.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -420,6 +444,9 @@ def main():
     # per-step host intervals (completion to completion; with calls in flight the first one carries the fill)
     per = [1000.0 * (b - a) for a, b in zip([t0] + marks[:-1], marks)]
     steady = per[1:] if len(per) > 2 else per
+    if args.dump_outputs and rank == 0:
+        # (the merged multi-GPU table comes in the order in which the ranks met its keys: sorted, as the parity check below does)
+        dump_outputs(args.dump_outputs, sorted(reducer.rows(*rows)) if sharded else rows.to_list(), names)
 
     # ---- multi-GPU (torch form): the merged table of the LAST step against ONE call over the union of the ranks' reads of
     # that step, run on rank 0 (after the timed region; the native form checks itself the same way).  A failure here is

@@ -1,7 +1,7 @@
 """The reference's remaining unit-test literals, held against BOTH the CPU oracle and libnimble_host.so (no GPU).
 
 Each case restates one test of the reference (file:line in its docstring), with the reference's inputs and expected values:
-  parse_calls                      /root/reference/src/align.rs:1233-1252
+  parse_calls                      src/align.rs:1233-1252
   unmap x3                         src/align.rs:1533-1608
   get_reference_sequence_data x2   src/utils.rs:127-164
   sort_score_vector x6             src/utils.rs:283-360

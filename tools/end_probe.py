@@ -1,7 +1,6 @@
 """How long does score_call_end take on the host: with the GPU idle, and with the next call running behind it?"""
 import importlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 nim = importlib.import_module("nimble-aligner_amd")
 synth = importlib.import_module("nimble-aligner_amd.synth")
